@@ -361,8 +361,27 @@ def dp_verify(model, ro, T, N, hp, world, rank, comm):
     return out
 
 
-def run_ppo2(workload, total_envs, T, steps, warmup, chunk, world, rank, comm, want_prof):
-    """-> dict with value / timing / roofline pieces of one PPO2-update measurement"""
+DUMP_LIMIT_BYTES = 60 * 2 ** 20      # --dump-outputs stays under 64 MB in all, .npy headers included
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: every array as <out_dir>/<name>.npy in float32 (float64 stays float64).  An array larger than its
+    share of DUMP_LIMIT_BYTES is replaced by a fixed seeded sample of its entries, so equal shapes give equal samples."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    share = DUMP_LIMIT_BYTES // len(arrays)
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        a = a.astype(np.float64 if a.dtype == np.float64 else np.float32)
+        n = share // a.itemsize
+        if a.size > n:
+            a = a.ravel()[np.sort(np.random.RandomState(0).choice(a.size, n, replace=False))]
+        np.save(os.path.join(out_dir, name + '.npy'), a)
+
+
+def run_ppo2(workload, total_envs, T, steps, warmup, chunk, world, rank, comm, want_prof, dump_dir=None):
+    """-> dict with value / timing / roofline pieces of one PPO2-update measurement; with `dump_dir`, rank 0 also writes what
+    the last timed update computed (dump_outputs): its loss statistics, the parameters it left and the GAE returns it trained on"""
     import numpy as np
     import torch
     from baselines_amd import _lib, ops
@@ -527,6 +546,9 @@ def run_ppo2(workload, total_envs, T, steps, warmup, chunk, world, rank, comm, w
         gc.unfreeze()                              # the frozen set is this timing window's only (config.host_gc says so)
     dt = t1 - t0
     device_state = sampler.stop(t0, t1) if sampler else None
+    if dump_dir and rank == 0:          # before the untimed profiling update below moves the parameters
+        dump_outputs(dump_dir, {'loss': lossvals.cpu().numpy(), 'params': model.params.cpu().numpy(),
+                                'returns': ro.returns.cpu().numpy()})
     prof = {}
     prof_steps = steps
     if want_prof:
@@ -768,7 +790,11 @@ def main():
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--no-prof', action='store_true', help='do not record HIP events per kernel in the timed region')
     ap.add_argument('--no-other-configs', action='store_true', help='skip the short runs of the other BASELINE configs')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps write what the last one computed as DIR/<name>.npy (float32, at most 64 MB)')
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be >= 1 and --warmup >= 0')
 
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
         _relaunch(args)
@@ -814,7 +840,8 @@ def main():
     sites, arith_text, arith_short = arithmetic_mode(_lib)
     total_envs = args.num_envs or (4096 if args.workload == 'atari' else 1024)
     T = args.nsteps
-    res = run_ppo2(args.workload, total_envs, T, args.steps, args.warmup, args.chunk, world, rank, comm, not args.no_prof)
+    res = run_ppo2(args.workload, total_envs, T, args.steps, args.warmup, args.chunk, world, rank, comm, not args.no_prof,
+                   dump_dir=args.dump_outputs)
 
     if rank == 0:
         hp = res['hp']
