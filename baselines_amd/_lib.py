@@ -44,6 +44,7 @@ SIGNATURES = {
     'mrl_device_count': (c_int, []),
     'mrl_gae': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_double, c_double, c_void_p, c_void_p,
                         c_int, c_int, c_void_p]),
+    'mrl_nstep_returns': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_double, c_void_p, c_int, c_int, c_void_p]),
     'mrl_gather_rows': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
     'mrl_sf01': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
     'mrl_model_create': (c_int, [ctypes.POINTER(ModelDesc), ctypes.POINTER(c_void_p)]),
@@ -72,6 +73,15 @@ SIGNATURES = {
                                    c_float, c_float, c_float, c_void_p, c_void_p, c_void_p]),
     'mrl_adam_clip_step_dev': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_long, c_void_p, c_float, c_float,
                                        c_float, c_float, c_float, c_void_p, c_void_p, c_void_p]),
+    'mrl_model_grad_a2c': (c_int, [c_void_p] * 8 + [c_int, c_void_p, c_int, c_int, c_int, c_float, c_float, c_void_p,
+                                                    c_void_p, c_void_p, c_size_t, c_int, c_void_p]),
+    'mrl_rmsprop_clip_step': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_long, c_float, c_float, c_float,
+                                      c_float, c_float, c_float, c_void_p, c_void_p, c_void_p]),
+    'mrl_rmsprop_clip_step_dev': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_long, c_void_p, c_float, c_float,
+                                          c_float, c_float, c_float, c_void_p, c_void_p, c_void_p]),
+    'mrl_model_train_step_a2c': (c_int, [c_void_p] * 11 + [c_int, c_void_p, c_int, c_int, c_int, c_float, c_float, c_float,
+                                                           c_void_p, c_float, c_float, c_float, c_float, c_void_p, c_void_p,
+                                                           c_void_p, c_size_t, c_int, c_void_p]),
     'mrl_qnet_create': (c_int, [ctypes.POINTER(QNetDesc), ctypes.POINTER(c_void_p)]),
     'mrl_qnet_destroy': (None, [c_void_p]),
     'mrl_qnet_num_params': (c_long, [c_void_p]),

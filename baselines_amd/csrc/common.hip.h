@@ -61,5 +61,9 @@ struct ProfScope {
 int adam_clip_apply(float* params, float* grads, float* m, float* v, long P, float alpha, const float* alpha_dev,
                     float beta1, float beta2, float eps, float max_grad_norm, float total_weight, float* gnorm_out,
                     void* scratch, const double* ready_part, int ready_npart, hipStream_t st);
+// clip_by_global_norm + TF-1 RMSProp (rollout.hip), same conventions
+int rmsprop_clip_apply(float* params, float* grads, float* ms, float* mom, long P, float lr, const float* lr_dev, float decay,
+                       float momentum, float eps, float max_grad_norm, float total_weight, float* gnorm_out, void* scratch,
+                       const double* ready_part, int ready_npart, hipStream_t st);
 
 }  // namespace mrl

@@ -838,6 +838,14 @@ __device__ __forceinline__ void head_tile_forward(const HeadArgs& a, const HeadL
 #define MRL_HALF_LOG_2PI 0.9189385332046727f      /* f32(0.5*log(2*pi)) */
 #define MRL_HALF_LOG_2PIE 1.4189385332046727f     /* f32(0.5*log(2*pi*e)) */
 
+// Loss kinds of the head kernels.  LOSS_PPO2: ppo2/model.py:57-91 (minibatch-normalised advantages, clipped ratio and
+// value).  LOSS_A2C: a2c/a2c.py:57-68 -- adv = R - V of the rollout (not normalised, a2c.py:93), pg = mean(adv * neglogp),
+// vf = mean((v - R)^2) (losses.mean_squared_error: no 0.5, no clipping), hence per sample dnlp = adv / B and
+// dv = 2 vf_coef (v - R) / B; statistics (adv * nlp, (v - R)^2, H).  The PPO2 instantiations are the kernels as they were:
+// every A2C difference sits behind `if constexpr`.
+constexpr int LOSS_PPO2 = 0, LOSS_A2C = 1;
+
+template <int LOSS>
 __global__ __launch_bounds__(256) void heads_train_kernel(HeadArgs a) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     __shared__ double sred[4];
@@ -848,7 +856,8 @@ __global__ __launch_bounds__(256) void heads_train_kernel(HeadArgs a) {
     for (int q = tid; q < a.HP; q += 256) L.hacc[q] = 0.f;
     double st[5] = {0, 0, 0, 0, 0};
     const int ntiles = (a.Bc + a.TS - 1) / a.TS;
-    const float mean = a.advstat[0], sd = a.advstat[1] + 1e-8f;
+    float mean = 0.f, sd = 1.f;
+    if constexpr (LOSS == LOSS_PPO2) { mean = a.advstat[0]; sd = a.advstat[1] + 1e-8f; }
     const float eps = a.cliprange;
     const float ce = a.ent_coef * a.invB;
     __syncthreads();
@@ -859,8 +868,9 @@ __global__ __launch_bounds__(256) void heads_train_kernel(HeadArgs a) {
             const int s = tid;
             const int b = s0 + s;
             const long r = a.idx ? envmajor_to_row(a.idx[b], a.T, a.N) : a.row0 + b;
-            const float R = a.returns[r], oldv = a.values[r], oldnlp = a.neglogp[r];
-            const float adv = ((R - oldv) - mean) / sd;
+            const float R = a.returns[r], oldv = a.values[r];
+            const float oldnlp = LOSS == LOSS_PPO2 ? a.neglogp[r] : 0.f;
+            const float adv = LOSS == LOSS_PPO2 ? ((R - oldv) - mean) / sd : R - oldv;
             float* pi = L.pi + s * a.nact;
             float* dpi = L.dpi + s * a.nact;
             float nlp, H;
@@ -877,21 +887,30 @@ __global__ __launch_bounds__(256) void heads_train_kernel(HeadArgs a) {
                     float a0 = pi[j] - mx;
                     H += (expf(a0) / z0) * (logz - a0);
                 }
-                const float ratio = expf(oldnlp - nlp);
-                const float pg1 = -adv * ratio;
-                const float rc = fminf(fmaxf(ratio, 1.f - eps), 1.f + eps);
-                const float pg2 = -adv * rc;
-                float dr = (pg1 >= pg2) ? -adv : ((ratio >= 1.f - eps && ratio <= 1.f + eps) ? -adv : 0.f);
-                const float dnlp = dr * (-ratio) * a.invB;
+                float ratio = 0.f, pg1 = 0.f, pg2 = 0.f, dnlp;
+                if constexpr (LOSS == LOSS_PPO2) {
+                    ratio = expf(oldnlp - nlp);
+                    pg1 = -adv * ratio;
+                    const float rc = fminf(fmaxf(ratio, 1.f - eps), 1.f + eps);
+                    pg2 = -adv * rc;
+                    float dr = (pg1 >= pg2) ? -adv : ((ratio >= 1.f - eps && ratio <= 1.f + eps) ? -adv : 0.f);
+                    dnlp = dr * (-ratio) * a.invB;
+                } else {
+                    dnlp = adv * a.invB;
+                }
                 for (int j = 0; j < a.nact; ++j) {
                     float a0 = pi[j] - mx;
                     float p = expf(a0) / z0;
                     float logp = a0 - logz;
                     dpi[j] = dnlp * (p - (j == act ? 1.f : 0.f)) + ce * p * (logp + H);
                 }
-                st[0] += (double)fmaxf(pg1, pg2);
-                st[3] += 0.5 * (double)((nlp - oldnlp) * (nlp - oldnlp));
-                st[4] += (fabsf(ratio - 1.f) > eps) ? 1.0 : 0.0;
+                if constexpr (LOSS == LOSS_PPO2) {
+                    st[0] += (double)fmaxf(pg1, pg2);
+                    st[3] += 0.5 * (double)((nlp - oldnlp) * (nlp - oldnlp));
+                    st[4] += (fabsf(ratio - 1.f) > eps) ? 1.0 : 0.0;
+                } else {
+                    st[0] += (double)(adv * nlp);
+                }
             } else if (a.pd_kind == MRL_PD_MULTICATEGORICAL || a.pd_kind == MRL_PD_BERNOULLI) {
                 // distributions.py:206-225 / 253-276: neglogp and entropy are SUMS over independent sub-distributions; the
                 // gradient of a slice is the categorical one with that slice's own entropy.  Two passes: the sums first (they
@@ -925,12 +944,17 @@ __global__ __launch_bounds__(256) void heads_train_kernel(HeadArgs a) {
                         H += sp - l * p;
                     }
                 }
-                const float ratio = expf(oldnlp - nlp);
-                const float pg1 = -adv * ratio;
-                const float rc = fminf(fmaxf(ratio, 1.f - eps), 1.f + eps);
-                const float pg2 = -adv * rc;
-                float dr = (pg1 >= pg2) ? -adv : ((ratio >= 1.f - eps && ratio <= 1.f + eps) ? -adv : 0.f);
-                const float dnlp = dr * (-ratio) * a.invB;
+                float ratio = 0.f, pg1 = 0.f, pg2 = 0.f, dnlp;
+                if constexpr (LOSS == LOSS_PPO2) {
+                    ratio = expf(oldnlp - nlp);
+                    pg1 = -adv * ratio;
+                    const float rc = fminf(fmaxf(ratio, 1.f - eps), 1.f + eps);
+                    pg2 = -adv * rc;
+                    float dr = (pg1 >= pg2) ? -adv : ((ratio >= 1.f - eps && ratio <= 1.f + eps) ? -adv : 0.f);
+                    dnlp = dr * (-ratio) * a.invB;
+                } else {
+                    dnlp = adv * a.invB;
+                }
                 o = 0;
                 for (int q = 0; q < nsub; ++q) {
                     if (multi) {
@@ -954,9 +978,13 @@ __global__ __launch_bounds__(256) void heads_train_kernel(HeadArgs a) {
                         dpi[q] = dnlp * (p - (float)x[q]) + ce * l * p * (1.f - p);
                     }
                 }
-                st[0] += (double)fmaxf(pg1, pg2);
-                st[3] += 0.5 * (double)((nlp - oldnlp) * (nlp - oldnlp));
-                st[4] += (fabsf(ratio - 1.f) > eps) ? 1.0 : 0.0;
+                if constexpr (LOSS == LOSS_PPO2) {
+                    st[0] += (double)fmaxf(pg1, pg2);
+                    st[3] += 0.5 * (double)((nlp - oldnlp) * (nlp - oldnlp));
+                    st[4] += (fabsf(ratio - 1.f) > eps) ? 1.0 : 0.0;
+                } else {
+                    st[0] += (double)(adv * nlp);
+                }
             } else {
                 const float* x = static_cast<const float*>(a.actions) + r * a.nact;
                 float* dls = L.dls + s * a.nact;
@@ -970,30 +998,45 @@ __global__ __launch_bounds__(256) void heads_train_kernel(HeadArgs a) {
                     H += ls + MRL_HALF_LOG_2PIE;
                 }
                 nlp = 0.5f * ssum + MRL_HALF_LOG_2PI * (float)a.nact + lsum;
-                const float ratio = expf(oldnlp - nlp);
-                const float pg1 = -adv * ratio;
-                const float rc = fminf(fmaxf(ratio, 1.f - eps), 1.f + eps);
-                const float pg2 = -adv * rc;
-                float dr = (pg1 >= pg2) ? -adv : ((ratio >= 1.f - eps && ratio <= 1.f + eps) ? -adv : 0.f);
-                const float dnlp = dr * (-ratio) * a.invB;
+                float ratio = 0.f, pg1 = 0.f, pg2 = 0.f, dnlp;
+                if constexpr (LOSS == LOSS_PPO2) {
+                    ratio = expf(oldnlp - nlp);
+                    pg1 = -adv * ratio;
+                    const float rc = fminf(fmaxf(ratio, 1.f - eps), 1.f + eps);
+                    pg2 = -adv * rc;
+                    float dr = (pg1 >= pg2) ? -adv : ((ratio >= 1.f - eps && ratio <= 1.f + eps) ? -adv : 0.f);
+                    dnlp = dr * (-ratio) * a.invB;
+                } else {
+                    dnlp = adv * a.invB;
+                }
                 for (int k = 0; k < a.nact; ++k) {
                     float sdk = expf(L.logstd[k]);
                     float u = (x[k] - pi[k]) / sdk;
                     dpi[k] = dnlp * (-(u / sdk));
                     dls[k] = dnlp * (1.f - u * u) - ce;
                 }
-                st[0] += (double)fmaxf(pg1, pg2);
-                st[3] += 0.5 * (double)((nlp - oldnlp) * (nlp - oldnlp));
-                st[4] += (fabsf(ratio - 1.f) > eps) ? 1.0 : 0.0;
+                if constexpr (LOSS == LOSS_PPO2) {
+                    st[0] += (double)fmaxf(pg1, pg2);
+                    st[3] += 0.5 * (double)((nlp - oldnlp) * (nlp - oldnlp));
+                    st[4] += (fabsf(ratio - 1.f) > eps) ? 1.0 : 0.0;
+                } else {
+                    st[0] += (double)(adv * nlp);
+                }
             }
-            // value loss (model.py:68-75)
+            // value loss (model.py:68-75 | a2c.py:66)
             const float v = L.v[s];
-            const float dvc = fminf(fmaxf(v - oldv, -eps), eps);
-            const float vclip = oldv + dvc;
-            const float l1 = (v - R) * (v - R), l2 = (vclip - R) * (vclip - R);
-            float dl = (l1 >= l2) ? (v - R) : ((v - oldv >= -eps && v - oldv <= eps) ? (vclip - R) : 0.f);
-            L.dv[s] = a.vf_coef * a.invB * dl;
-            st[1] += 0.5 * (double)fmaxf(l1, l2);
+            if constexpr (LOSS == LOSS_PPO2) {
+                const float dvc = fminf(fmaxf(v - oldv, -eps), eps);
+                const float vclip = oldv + dvc;
+                const float l1 = (v - R) * (v - R), l2 = (vclip - R) * (vclip - R);
+                float dl = (l1 >= l2) ? (v - R) : ((v - oldv >= -eps && v - oldv <= eps) ? (vclip - R) : 0.f);
+                L.dv[s] = a.vf_coef * a.invB * dl;
+                st[1] += 0.5 * (double)fmaxf(l1, l2);
+            } else {
+                const float dl = v - R;
+                L.dv[s] = 2.f * a.vf_coef * a.invB * dl;
+                st[1] += (double)(dl * dl);
+            }
             st[2] += (double)H;
         }
         __syncthreads();
@@ -1068,7 +1111,7 @@ __global__ __launch_bounds__(256) void heads_train_kernel(HeadArgs a) {
 // in registers; the nact+1 dot products are butterfly-reduced across the wave (every lane ends with the same sums),
 // every lane evaluates the per-sample loss algebra of model.py:57-91 redundantly, writes its slice of the masked dz row
 // and accumulates its slice of the head-weight gradients in registers.  Fixed summation orders: run-to-run identical.
-template <int KPL>
+template <int KPL, int LOSS>
 __global__ __launch_bounds__(256) void heads_train_wave_kernel(HeadArgs a) {
     constexpr int NA = 8;
     extern __shared__ __attribute__((aligned(16))) float smem[];     // [4 waves][HP] head-gradient partials
@@ -1092,7 +1135,8 @@ __global__ __launch_bounds__(256) void heads_train_wave_kernel(HeadArgs a) {
     for (int j = 0; j < NA; ++j) { bpi[j] = j < nact ? a.bpi[j] : 0.f; gb[j] = 0.f; }
     const float bv = a.bvf[0];
     double st[5] = {0, 0, 0, 0, 0};
-    const float mean = a.advstat[0], sd = a.advstat[1] + 1e-8f;
+    float mean = 0.f, sd = 1.f;
+    if constexpr (LOSS == LOSS_PPO2) { mean = a.advstat[0]; sd = a.advstat[1] + 1e-8f; }
     const float eps = a.cliprange;
     const float ce = a.ent_coef * a.invB;
     const int nwaves = gridDim.x * 4;
@@ -1105,7 +1149,8 @@ __global__ __launch_bounds__(256) void heads_train_wave_kernel(HeadArgs a) {
             x[q * 4 + 0] = v.x; x[q * 4 + 1] = v.y; x[q * 4 + 2] = v.z; x[q * 4 + 3] = v.w;
         }
         const long r = a.idx ? envmajor_to_row(a.idx[b], a.T, a.N) : a.row0 + b;
-        const float R = a.returns[r], oldv = a.values[r], oldnlp = a.neglogp[r];
+        const float R = a.returns[r], oldv = a.values[r];
+        const float oldnlp = LOSS == LOSS_PPO2 ? a.neglogp[r] : 0.f;
         const int act = static_cast<const int32_t*>(a.actions)[r];
         float pi[NA], v = 0.f;
 #pragma unroll
@@ -1128,7 +1173,7 @@ __global__ __launch_bounds__(256) void heads_train_wave_kernel(HeadArgs a) {
         for (int j = 0; j < NA; ++j) pi[j] += bpi[j];
         v += bv;
         // ---- per-sample loss algebra, identical in every lane (same formulas as heads_train_kernel)
-        const float adv = ((R - oldv) - mean) / sd;
+        const float adv = LOSS == LOSS_PPO2 ? ((R - oldv) - mean) / sd : R - oldv;
         float mx = pi[0];
 #pragma unroll
         for (int j = 1; j < NA; ++j) if (j < nact) mx = fmaxf(mx, pi[j]);
@@ -1147,12 +1192,17 @@ __global__ __launch_bounds__(256) void heads_train_wave_kernel(HeadArgs a) {
                 const float a0 = pi[j] - mx;
                 H += (expf(a0) / z0) * (logz - a0);
             }
-        const float ratio = expf(oldnlp - nlp);
-        const float pg1 = -adv * ratio;
-        const float rc = fminf(fmaxf(ratio, 1.f - eps), 1.f + eps);
-        const float pg2 = -adv * rc;
-        const float dr = (pg1 >= pg2) ? -adv : ((ratio >= 1.f - eps && ratio <= 1.f + eps) ? -adv : 0.f);
-        const float dnlp = dr * (-ratio) * a.invB;
+        float ratio = 0.f, pg1 = 0.f, pg2 = 0.f, dnlp;
+        if constexpr (LOSS == LOSS_PPO2) {
+            ratio = expf(oldnlp - nlp);
+            pg1 = -adv * ratio;
+            const float rc = fminf(fmaxf(ratio, 1.f - eps), 1.f + eps);
+            pg2 = -adv * rc;
+            const float dr = (pg1 >= pg2) ? -adv : ((ratio >= 1.f - eps && ratio <= 1.f + eps) ? -adv : 0.f);
+            dnlp = dr * (-ratio) * a.invB;
+        } else {
+            dnlp = adv * a.invB;
+        }
         float dpi[NA];
 #pragma unroll
         for (int j = 0; j < NA; ++j) {
@@ -1164,16 +1214,25 @@ __global__ __launch_bounds__(256) void heads_train_wave_kernel(HeadArgs a) {
                 dpi[j] = dnlp * (p - (j == act ? 1.f : 0.f)) + ce * p * (logp + H);
             }
         }
-        const float dvc = fminf(fmaxf(v - oldv, -eps), eps);
-        const float vclip = oldv + dvc;
-        const float l1 = (v - R) * (v - R), l2 = (vclip - R) * (vclip - R);
-        const float dl = (l1 >= l2) ? (v - R) : ((v - oldv >= -eps && v - oldv <= eps) ? (vclip - R) : 0.f);
-        const float dv = a.vf_coef * a.invB * dl;
-        st[0] += (double)fmaxf(pg1, pg2);
-        st[1] += 0.5 * (double)fmaxf(l1, l2);
-        st[2] += (double)H;
-        st[3] += 0.5 * (double)((nlp - oldnlp) * (nlp - oldnlp));
-        st[4] += (fabsf(ratio - 1.f) > eps) ? 1.0 : 0.0;
+        float dv;
+        if constexpr (LOSS == LOSS_PPO2) {
+            const float dvc = fminf(fmaxf(v - oldv, -eps), eps);
+            const float vclip = oldv + dvc;
+            const float l1 = (v - R) * (v - R), l2 = (vclip - R) * (vclip - R);
+            const float dl = (l1 >= l2) ? (v - R) : ((v - oldv >= -eps && v - oldv <= eps) ? (vclip - R) : 0.f);
+            dv = a.vf_coef * a.invB * dl;
+            st[0] += (double)fmaxf(pg1, pg2);
+            st[1] += 0.5 * (double)fmaxf(l1, l2);
+            st[2] += (double)H;
+            st[3] += 0.5 * (double)((nlp - oldnlp) * (nlp - oldnlp));
+            st[4] += (fabsf(ratio - 1.f) > eps) ? 1.0 : 0.0;
+        } else {
+            const float dl = v - R;
+            dv = 2.f * a.vf_coef * a.invB * dl;
+            st[0] += (double)(adv * nlp);
+            st[1] += (double)(dl * dl);
+            st[2] += (double)H;
+        }
         // ---- dz of the latent layer (masked by act') and this lane's slice of the head gradients
         float g[KPL];
 #pragma unroll
@@ -1225,7 +1284,7 @@ __global__ __launch_bounds__(256) void heads_train_wave_kernel(HeadArgs a) {
 // one-sample kernel evaluates redundantly -- is evaluated ONCE for both (lane half = sample).  The per-sample scalars every lane needs
 // afterwards (dpi, dv, the five statistics) come back as wave-uniform values (v_readlane of lane 0 / lane 32) and multiply as scalar
 // operands.  Two independent dependency chains per wave also hide each other's latencies (the kernel runs two waves per SIMD).
-template <int KPL, int NA>
+template <int KPL, int NA, int LOSS>
 __global__ __launch_bounds__(256) void heads_train_wave2_kernel(HeadArgs a) {
     extern __shared__ __attribute__((aligned(16))) float smem[];     // [4 waves][HP] head-gradient partials
     __shared__ double sst[4][5];
@@ -1249,7 +1308,8 @@ __global__ __launch_bounds__(256) void heads_train_wave2_kernel(HeadArgs a) {
     for (int j = 0; j < NA; ++j) { bpi[j] = j < nact ? a.bpi[j] : 0.f; gb[j] = 0.f; }
     const float bv = a.bvf[0];
     double st[5] = {0, 0, 0, 0, 0};
-    const float mean = a.advstat[0], sd = a.advstat[1] + 1e-8f;
+    float mean = 0.f, sd = 1.f;
+    if constexpr (LOSS == LOSS_PPO2) { mean = a.advstat[0]; sd = a.advstat[1] + 1e-8f; }
     const float eps = a.cliprange;
     const float ce = a.ent_coef * a.invB;
     const int nwaves = gridDim.x * 4;
@@ -1270,7 +1330,8 @@ __global__ __launch_bounds__(256) void heads_train_wave2_kernel(HeadArgs a) {
         }
         const int bm = hiB ? b2 : b;                                 // the sample this lane's algebra belongs to
         const long r = a.idx ? envmajor_to_row(a.idx[bm], a.T, a.N) : a.row0 + bm;
-        const float R = a.returns[r], oldv = a.values[r], oldnlp = a.neglogp[r];
+        const float R = a.returns[r], oldv = a.values[r];
+        const float oldnlp = LOSS == LOSS_PPO2 ? a.neglogp[r] : 0.f;
         const int act = static_cast<const int32_t*>(a.actions)[r];
         float pi[NA], v;
         {
@@ -1303,7 +1364,7 @@ __global__ __launch_bounds__(256) void heads_train_wave2_kernel(HeadArgs a) {
         for (int j = 0; j < NA; ++j) pi[j] += bpi[j];
         v += bv;
         // ---- per-sample loss algebra (formulas and evaluation order of heads_train_wave_kernel), once per lane half
-        const float adv = ((R - oldv) - mean) / sd;
+        const float adv = LOSS == LOSS_PPO2 ? ((R - oldv) - mean) / sd : R - oldv;
         float mx = pi[0];
 #pragma unroll
         for (int j = 1; j < NA; ++j) if (j < nact) mx = fmaxf(mx, pi[j]);
@@ -1322,12 +1383,17 @@ __global__ __launch_bounds__(256) void heads_train_wave2_kernel(HeadArgs a) {
                 const float a0 = pi[j] - mx;
                 H += (expf(a0) / z0) * (logz - a0);
             }
-        const float ratio = expf(oldnlp - nlp);
-        const float pg1 = -adv * ratio;
-        const float rc = fminf(fmaxf(ratio, 1.f - eps), 1.f + eps);
-        const float pg2 = -adv * rc;
-        const float dr = (pg1 >= pg2) ? -adv : ((ratio >= 1.f - eps && ratio <= 1.f + eps) ? -adv : 0.f);
-        const float dnlp = dr * (-ratio) * a.invB;
+        float ratio = 0.f, pg1 = 0.f, pg2 = 0.f, dnlp;
+        if constexpr (LOSS == LOSS_PPO2) {
+            ratio = expf(oldnlp - nlp);
+            pg1 = -adv * ratio;
+            const float rc = fminf(fmaxf(ratio, 1.f - eps), 1.f + eps);
+            pg2 = -adv * rc;
+            const float dr = (pg1 >= pg2) ? -adv : ((ratio >= 1.f - eps && ratio <= 1.f + eps) ? -adv : 0.f);
+            dnlp = dr * (-ratio) * a.invB;
+        } else {
+            dnlp = adv * a.invB;
+        }
         float dpi[NA];
 #pragma unroll
         for (int j = 0; j < NA; ++j) {
@@ -1339,23 +1405,36 @@ __global__ __launch_bounds__(256) void heads_train_wave2_kernel(HeadArgs a) {
                 dpi[j] = dnlp * (p - (j == act ? 1.f : 0.f)) + ce * p * (logp + H);
             }
         }
-        const float dvc = fminf(fmaxf(v - oldv, -eps), eps);
-        const float vclip = oldv + dvc;
-        const float l1 = (v - R) * (v - R), l2 = (vclip - R) * (vclip - R);
-        const float dl = (l1 >= l2) ? (v - R) : ((v - oldv >= -eps && v - oldv <= eps) ? (vclip - R) : 0.f);
-        const float dv = a.vf_coef * a.invB * dl;
-        const float s0 = fmaxf(pg1, pg2), s1 = fmaxf(l1, l2), s3 = (nlp - oldnlp) * (nlp - oldnlp);
-        const float s4 = (fabsf(ratio - 1.f) > eps) ? 1.f : 0.f;
+        float dv, s0, s1, s3 = 0.f, s4 = 0.f;
+        if constexpr (LOSS == LOSS_PPO2) {
+            const float dvc = fminf(fmaxf(v - oldv, -eps), eps);
+            const float vclip = oldv + dvc;
+            const float l1 = (v - R) * (v - R), l2 = (vclip - R) * (vclip - R);
+            const float dl = (l1 >= l2) ? (v - R) : ((v - oldv >= -eps && v - oldv <= eps) ? (vclip - R) : 0.f);
+            dv = a.vf_coef * a.invB * dl;
+            s0 = fmaxf(pg1, pg2); s1 = fmaxf(l1, l2); s3 = (nlp - oldnlp) * (nlp - oldnlp);
+            s4 = (fabsf(ratio - 1.f) > eps) ? 1.f : 0.f;
+        } else {
+            const float dl = v - R;
+            dv = 2.f * a.vf_coef * a.invB * dl;
+            s0 = adv * nlp; s1 = dl * dl;
+        }
         // ---- statistics in the one-sample kernel's order: sample A, then sample B
 #pragma unroll
         for (int half = 0; half < 2; ++half) {
             if (half == 1 && !hasB) continue;
             const int src = half * 32;
-            st[0] += (double)bcast(s0, src);
-            st[1] += 0.5 * (double)bcast(s1, src);
-            st[2] += (double)bcast(H, src);
-            st[3] += 0.5 * (double)bcast(s3, src);
-            st[4] += (double)bcast(s4, src);
+            if constexpr (LOSS == LOSS_PPO2) {
+                st[0] += (double)bcast(s0, src);
+                st[1] += 0.5 * (double)bcast(s1, src);
+                st[2] += (double)bcast(H, src);
+                st[3] += 0.5 * (double)bcast(s3, src);
+                st[4] += (double)bcast(s4, src);
+            } else {
+                st[0] += (double)bcast(s0, src);
+                st[1] += (double)bcast(s1, src);
+                st[2] += (double)bcast(H, src);
+            }
         }
         // ---- dz of the latent layer (masked by act') and this lane's slice of the head gradients: sample A, then sample B
 #pragma unroll
@@ -2738,14 +2817,16 @@ static int model_grad_range(const mrl_model* m, const float* params, const void*
                             const int64_t* idx, int Bstat, int mb0, int mbn, int T, int N, float cliprange, float ent_coef,
                             float vf_coef, float* grads_out, float* stats_out, void* workspace,
                             size_t workspace_bytes, int chunk, void* stream, bool want_sq = false, int* sqn_out = nullptr,
-                            const RnnIn* rnn = nullptr) {
+                            const RnnIn* rnn = nullptr, int loss = LOSS_PPO2) {
     if (sqn_out) *sqn_out = 0;
+    const bool a2c = loss == LOSS_A2C;              // a2c/a2c.py:57-68: no advantage statistics, no neglogp / cliprange
+    if (a2c && m && m->comm) return MRL_EUNSUP;     // the reference's A2C has no multi-rank path
     if (m && m->pi.lstm) {
         // recurrent policies: whole minibatch of nseq trajectories of B/nseq steps each, sample b = seq*steps + t, one chunk
         if (!rnn || !rnn->masks || rnn->nseq <= 0 || mb0 != 0 || mbn != Bstat || Bstat % rnn->nseq != 0) return MRL_EINVAL;
         if (Bstat > chunk) return MRL_EUNSUP;
     } else if (rnn) return MRL_EINVAL;
-    if (!m || !params || !obs || !actions || !returns || !values || !neglogpacs || !grads_out || !stats_out ||
+    if (!m || !params || !obs || !actions || !returns || !values || (!neglogpacs && !a2c) || !grads_out || !stats_out ||
         !workspace || Bstat <= 0 || chunk <= 0 || mb0 < 0 || mbn <= 0 || mb0 + mbn > Bstat)
         return MRL_EINVAL;
     if (idx && (T <= 0 || N <= 0)) return MRL_EINVAL;
@@ -2776,14 +2857,16 @@ static int model_grad_range(const mrl_model* m, const float* params, const void*
     const bool mlp_fused = [&] {
         const mrl_model_desc& d = m->d;
         const int K0 = (int)m->ob_elems, nets = m->vf_copy ? 2 : 1, ntiles = (B0 + 31) / 32;
-        return get_option("mlp_fused", "MRL_MLP_FUSED", 1) && d.network == MRL_NET_MLP && d.num_layers == 2 && !d.layer_norm && d.pd_kind <= MRL_PD_DIAG_GAUSSIAN &&
+        return !a2c && get_option("mlp_fused", "MRL_MLP_FUSED", 1) && d.network == MRL_NET_MLP && d.num_layers == 2 && !d.layer_norm && d.pd_kind <= MRL_PD_DIAG_GAUSSIAN &&
                d.num_hidden == MLP_NH && d.activation == MRL_ACT_TANH && m->has_pi_head && d.nact <= 32 && K0 % 4 == 0 &&
                B0 <= chunk && ntiles <= MLP_MAX_TILES && mlp_step_lds_bytes(K0, nets) <= 160 * 1024 &&
                (size_t)ntiles * m->P <= ws.part_floats && (uintptr_t)params % 16 == 0 && (uintptr_t)obs % 16 == 0;
     }();
     const float* stat_ret = returns; const float* stat_val = values; const int64_t* stat_idx = idx;
     // minibatch advantage statistics (model.py:136-139)
-    if (!mlp_fused) {
+    if (a2c) {
+        MRL_HIP_CHECK(hipMemsetAsync(stats_acc, 0, 5 * sizeof(double), st));
+    } else if (!mlp_fused) {
         int G = std::min(ADV_G, (Bstat + 255) / 256);
         ProfScope* psadv = new ProfScope("adv_stats", 0.0, (idx ? 16.0 : 8.0) * Bstat, st);
         hipLaunchKernelGGL(advstat_part_kernel, dim3(G), dim3(256), 0, st, returns, values, idx, Bstat, T, N, advpart,
@@ -2801,7 +2884,7 @@ static int model_grad_range(const mrl_model* m, const float* params, const void*
             const size_t act_bytes = m->d.pd_kind == MRL_PD_CATEGORICAL ? 4 : m->d.pd_kind == MRL_PD_MULTICATEGORICAL ? 4 * (size_t)m->d.nsub : 4 * (size_t)m->d.nact;
             obs = (const char*)obs + (size_t)mb0 * ob_bytes;
             actions = (const char*)actions + (size_t)mb0 * act_bytes;
-            returns += mb0; values += mb0; neglogpacs += mb0;
+            returns += mb0; values += mb0; if (neglogpacs) neglogpacs += mb0;
         }
     }
     const float invB = 1.f / (float)B;
@@ -2863,7 +2946,7 @@ static int model_grad_range(const mrl_model* m, const float* params, const void*
         ctx.final_chunk = c0 + chunk >= B;
         In in;
         if (idx) {
-            if (c0 > 0 || !whole) {                      // chunk 0 of a whole minibatch was translated by advstat_part_kernel
+            if (c0 > 0 || !whole || a2c) {               // chunk 0 of a whole minibatch was translated by advstat_part_kernel
                 hipLaunchKernelGGL(translate_idx_kernel, dim3((Bc + 255) / 256), dim3(256), 0, st, idx + c0, Bc, T, N, ws.srow);
                 MRL_LAUNCH_CHECK();
             }
@@ -2899,7 +2982,7 @@ static int model_grad_range(const mrl_model* m, const float* params, const void*
         int ntiles = (Bc + a.TS - 1) / a.TS;
         int nblk = std::min(ntiles, HEAD_MAXBLK);
         if (lds > 64 * 1024) {
-            hipError_t e = hipFuncSetAttribute((const void*)heads_train_kernel,
+            hipError_t e = hipFuncSetAttribute(a2c ? (const void*)heads_train_kernel<LOSS_A2C> : (const void*)heads_train_kernel<LOSS_PPO2>,
                                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
             if (e != hipSuccess) return (int)e;
         }
@@ -2911,17 +2994,34 @@ static int model_grad_range(const mrl_model* m, const float* params, const void*
         {
             // algorithmic traffic: latent in, dz out, per-sample rollout scalars
             ProfScope ps("heads_loss", 0.0, (double)Bc * (8.0 * a.nlat + (a.shared ? 0 : 8.0 * a.nlatv) + 28.0), st);
-            if (wave_ok) {
+            if (wave_ok && a2c) {
+                // (the dynamic-LDS limit is raised to exactly what the launch takes: 7 / 8 actions need more than 64 KB, and a
+                // 160 KB request leaves no room for the kernels' static LDS)
                 const size_t wl = (size_t)4 * m->HP * sizeof(float);
-                if (wl > 64 * 1024) MRL_HIP_CHECK(raise_lds_limit((const void*)heads_train_wave_kernel<8>));        // once per (device, kernel)
+                if (wl > 64 * 1024)
+                    MRL_HIP_CHECK(hipFuncSetAttribute((const void*)heads_train_wave_kernel<8, LOSS_A2C>,
+                                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)wl));
                 if (a.nact <= 6 && get_option("heads_wave", "MRL_HEADS_WAVE", 2) >= 2) {
-                    if (wl > 64 * 1024) MRL_HIP_CHECK(raise_lds_limit((const void*)heads_train_wave2_kernel<8, 6>));
-                    hipLaunchKernelGGL((heads_train_wave2_kernel<8, 6>), dim3(nblk), dim3(256), wl, st, a);
+                    if (wl > 64 * 1024)
+                        MRL_HIP_CHECK(hipFuncSetAttribute((const void*)heads_train_wave2_kernel<8, 6, LOSS_A2C>,
+                                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)wl));
+                    hipLaunchKernelGGL((heads_train_wave2_kernel<8, 6, LOSS_A2C>), dim3(nblk), dim3(256), wl, st, a);
                 } else {
-                    hipLaunchKernelGGL(heads_train_wave_kernel<8>, dim3(nblk), dim3(256), wl, st, a);
+                    hipLaunchKernelGGL((heads_train_wave_kernel<8, LOSS_A2C>), dim3(nblk), dim3(256), wl, st, a);
                 }
+            } else if (wave_ok) {
+                const size_t wl = (size_t)4 * m->HP * sizeof(float);
+                if (wl > 64 * 1024) MRL_HIP_CHECK(raise_lds_limit((const void*)heads_train_wave_kernel<8, LOSS_PPO2>));   // once per (device, kernel)
+                if (a.nact <= 6 && get_option("heads_wave", "MRL_HEADS_WAVE", 2) >= 2) {
+                    if (wl > 64 * 1024) MRL_HIP_CHECK(raise_lds_limit((const void*)heads_train_wave2_kernel<8, 6, LOSS_PPO2>));
+                    hipLaunchKernelGGL((heads_train_wave2_kernel<8, 6, LOSS_PPO2>), dim3(nblk), dim3(256), wl, st, a);
+                } else {
+                    hipLaunchKernelGGL((heads_train_wave_kernel<8, LOSS_PPO2>), dim3(nblk), dim3(256), wl, st, a);
+                }
+            } else if (a2c) {
+                hipLaunchKernelGGL(heads_train_kernel<LOSS_A2C>, dim3(nblk), dim3(256), lds, st, a);
             } else {
-                hipLaunchKernelGGL(heads_train_kernel, dim3(nblk), dim3(256), lds, st, a);
+                hipLaunchKernelGGL(heads_train_kernel<LOSS_PPO2>, dim3(nblk), dim3(256), lds, st, a);
             }
         }
         MRL_LAUNCH_CHECK();
@@ -2935,7 +3035,8 @@ static int model_grad_range(const mrl_model* m, const float* params, const void*
         if (m->vf_copy && (rc = net_backward<kExp>(m, m->vf, in, params, ws.vf, ws, grads_out, Bc, accumulate, st, ctx, false)))
             return rc;
     }
-    hipLaunchKernelGGL(stats_finalize_kernel, dim3(1), dim3(64), 0, st, stats_acc, invB, stats_out);
+    // A2C: stats_out holds 3 values (pg_loss, vf_loss, entropy) -- only that many threads run
+    hipLaunchKernelGGL(stats_finalize_kernel, dim3(1), dim3(a2c ? 3 : 64), 0, st, stats_acc, invB, stats_out);
     MRL_LAUNCH_CHECK();
     if (ctx.comm) {        // the rest of the flat gradient, then the compute stream waits for both collectives
         int rc = comm_allreduce_async(ctx.comm, grads_out, ctx.early_layer >= 0 ? ctx.early_lo : m->P, ctx.rank_weight, st);
@@ -3021,6 +3122,43 @@ extern "C" int mrl_model_grad_rnn(const mrl_model* m, const float* params, const
     RnnIn r{states, masks, nseq};
     return model_grad_range(m, params, obs, actions, returns, values, neglogpacs, idx, B, 0, B, T, N, cliprange, ent_coef,
                             vf_coef, grads_out, stats_out, workspace, workspace_bytes, chunk, stream, false, nullptr, &r);
+}
+
+// ---- A2C --- a2c/a2c.py:57-86 (loss, gradients, clip_by_global_norm, RMSProp) -------------------------------------------
+// The whole rollout is one batch (a2c.py:94-96).  Recurrent policies train on nseq = N whole trajectories through the
+// RnnIn path (masks / states as mrl_model_grad_rnn); feedforward policies pass masks = states = NULL.
+extern "C" int mrl_model_grad_a2c(const mrl_model* m, const float* params, const void* obs, const void* actions,
+                                  const float* returns, const float* values, const uint8_t* masks, const float* states,
+                                  int nseq, const int64_t* idx, int B, int T, int N, float ent_coef, float vf_coef,
+                                  float* grads_out, float* stats_out, void* workspace, size_t workspace_bytes, int chunk,
+                                  void* stream) {
+    if (!m) return MRL_EINVAL;
+    RnnIn r{states, masks, nseq};
+    return model_grad_range(m, params, obs, actions, returns, values, nullptr, idx, B, 0, B, T, N, 0.f, ent_coef, vf_coef,
+                            grads_out, stats_out, workspace, workspace_bytes, chunk, stream, false, nullptr,
+                            m->pi.lstm ? &r : nullptr, LOSS_A2C);
+}
+
+extern "C" int mrl_model_train_step_a2c(const mrl_model* m, float* params, float* grads, float* rms_ms, float* rms_mom,
+                                        const void* obs, const void* actions, const float* returns, const float* values,
+                                        const uint8_t* masks, const float* states, int nseq, const int64_t* idx, int B,
+                                        int T, int N, float ent_coef, float vf_coef, float lr, const float* lr_dev,
+                                        float decay, float momentum, float eps, float max_grad_norm, float* stats_out,
+                                        float* gnorm_out, void* workspace, size_t workspace_bytes, int chunk, void* stream) {
+    if (!m || !rms_ms || !rms_mom) return MRL_EINVAL;
+    if (m->comm) return MRL_EUNSUP;
+    RnnIn r{states, masks, nseq};
+    int sqn = 0;
+    // (the LSTM's weight gradients are not written through the slab reductions: its norm takes the separate pass)
+    const bool want_sq = max_grad_norm >= 0.f && !m->pi.lstm;
+    int rc = model_grad_range(m, params, obs, actions, returns, values, nullptr, idx, B, 0, B, T, N, 0.f, ent_coef, vf_coef,
+                              grads, stats_out, workspace, workspace_bytes, chunk, stream, want_sq, &sqn,
+                              m->pi.lstm ? &r : nullptr, LOSS_A2C);
+    if (rc) return rc;
+    Ws ws;
+    carve(m, chunk, (char*)workspace, ws);
+    return rmsprop_clip_apply(params, grads, rms_ms, rms_mom, m->P, lr, lr_dev, decay, momentum, eps, max_grad_norm, 1.f,
+                              gnorm_out, ws.sqpart, sqn > 0 ? ws.sqpart : nullptr, sqn, (hipStream_t)stream);
 }
 
 #include "qnet.hip.h"

@@ -297,6 +297,49 @@ extern "C" int mrl_gae(const float* rew, const float* val, const uint8_t* done, 
 }
 
 // ------------------------------------------------------------------------------------------
+// A2C n-step discounted returns with bootstrap (a2c/runner.py:58-71 driving a2c/utils.py:147-153 discount_with_dones).
+// One environment per lane, the carry in f64 like the reference's Python floats, in the reference's operation order:
+//   r = 0;  if (!done_after[T-1]) r = last_val + (gamma * r) * 1.0          (the bootstrap element rewards + [value])
+//   for t = T-1 .. 0:  r = rew[t] + (gamma * r) * (1.0 - done_after[t]);  ret[t] = f32(r)   (round to nearest)
+// done_after[t] = the done flag step t returned = done[t + 1] (entering t + 1), last_done for t = T-1.  gamma <= 0: the
+// rewards unchanged (runner.py:58).  Explicit *_rn intrinsics: no contraction, and the sign of zero follows IEEE exactly
+// as in the reference (e.g. rew = -0.0 with a positive carry cut by a done gives +0.0).  At nsteps = 5 this is one
+// launch of a few microseconds; the operands of a step are one coalesced row per wave, nothing goes through LDS.
+// ------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(64) void nstep_returns_kernel(const float* __restrict__ rew, const uint8_t* __restrict__ done,
+                                                           const float* __restrict__ last_val,
+                                                           const uint8_t* __restrict__ last_done, double gamma, int discount,
+                                                           float* __restrict__ ret_out, int T, int N) {
+    const int e = blockIdx.x * 64 + threadIdx.x;
+    if (e >= N) return;
+    if (!discount) {
+        for (int t = 0; t < T; ++t) ret_out[(long)t * N + e] = rew[(long)t * N + e];
+        return;
+    }
+    uint8_t dn = last_done[e];                  // done flag returned by the step being accumulated
+    double r = 0.0;
+    if (!dn) r = __dadd_rn((double)last_val[e], __dmul_rn(__dmul_rn(gamma, r), 1.0));
+    for (int t = T - 1; t >= 0; --t) {
+        const long o = (long)t * N + e;
+        const float rw = rew[o];
+        const uint8_t d = done[o];
+        r = __dadd_rn((double)rw, __dmul_rn(__dmul_rn(gamma, r), dn ? 0.0 : 1.0));
+        ret_out[o] = (float)r;
+        dn = d;
+    }
+}
+
+extern "C" int mrl_nstep_returns(const float* rew, const uint8_t* done, const float* last_val, const uint8_t* last_done,
+                                 double gamma, float* ret_out, int T, int N, void* stream) {
+    if (T <= 0 || N <= 0 || !rew || !done || !last_val || !last_done || !ret_out) return MRL_EINVAL;
+    ProfScope ps("nstep_returns", 0.0, 10.0 * T * N + 5.0 * N, (hipStream_t)stream);
+    hipLaunchKernelGGL(nstep_returns_kernel, dim3((N + 63) / 64), dim3(64), 0, (hipStream_t)stream, rew, done, last_val,
+                       last_done, gamma, gamma > 0.0 ? 1 : 0, ret_out, T, N);
+    MRL_LAUNCH_CHECK();
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------------
 // Row gather / sf01.  Rows are moved 16 B per lane when row_bytes % 16 == 0, else 4 B / 1 B.
 // ------------------------------------------------------------------------------------------
 template <typename V>
@@ -524,4 +567,109 @@ extern "C" int mrl_adam_clip_step_dev(float* params, float* grads, float* m, flo
     if (!alpha_dev) return MRL_EINVAL;
     return adam_clip_apply(params, grads, m, v, P, 0.f, alpha_dev, beta1, beta2, eps, max_grad_norm, total_weight,
                            gnorm_out, scratch, nullptr, 0, (hipStream_t)stream);
+}
+
+// ------------------------------------------------------------------------------------------
+// clip_by_global_norm + RMSProp (a2c/a2c.py:76-86: tf.clip_by_global_norm, then tf.train.RMSPropOptimizer(lr, decay=alpha,
+// epsilon) -- TF 1.x training_ops ApplyRMSProp, momentum 0, not centered).  Per element, f32, in this order:
+//   g   := g / total_weight * scale           (scale = c * min(1/gn, 1/c), as the Adam step; max_grad_norm < 0: 1)
+//   ms  := ms + (g*g - ms) * (1 - decay)
+//   mom := mom * momentum + (lr * g) / sqrt(ms + epsilon)        (epsilon INSIDE the square root)
+//   p   := p - mom
+// The `rms` slot (ms) starts at ONES (rmsprop.py _create_slots: ones initializer), `momentum` at zeros.  Same launch shape
+// and norm partials as the Adam step above (re-reduced in a fixed order in every block); 28 B/param.
+// ------------------------------------------------------------------------------------------
+__device__ __forceinline__ void rmsprop_elem(float& p, float& g, float& ms, float& mom, float lr, float omd, float momentum,
+                                             float eps, float total_weight, float scale) {
+    float x = g;
+    if (total_weight != 1.f) x = x / total_weight;
+    x = x * scale;
+    g = x;          // the clipped, averaged gradient
+    ms = ms + (x * x - ms) * omd;
+    mom = mom * momentum + (lr * x) / sqrtf(ms + eps);
+    p = p - mom;
+}
+
+__global__ __launch_bounds__(256) void rmsprop_kernel(float* __restrict__ p, float* __restrict__ g, float* __restrict__ ms,
+                                                      float* __restrict__ mom, long P, float lr, float decay, float momentum,
+                                                      float eps, float max_grad_norm, float total_weight,
+                                                      const double* __restrict__ part, int npart,
+                                                      float* __restrict__ gnorm_out, const float* __restrict__ lr_dev) {
+    __shared__ double sh[4];
+    __shared__ float s_scale;
+    float scale = 1.f;
+    if (lr_dev) lr = lr_dev[0];               // step size kept in device memory (replayable launch graphs)
+    if (max_grad_norm >= 0.f) {
+        double s = 0.0;
+        for (int i = threadIdx.x; i < npart; i += 256) s += part[i];
+        double tot = block_sum_256(s, sh);
+        if (threadIdx.x == 0) {
+            float gn = (float)sqrt(tot);
+            s_scale = max_grad_norm * fminf(1.f / gn, 1.f / max_grad_norm);
+            if (gnorm_out && blockIdx.x == 0) gnorm_out[0] = gn;
+        }
+        __syncthreads();
+        scale = s_scale;
+    }
+    const float omd = 1.f - decay;
+    const long P4 = P >> 2;
+    float4* p4 = reinterpret_cast<float4*>(p);
+    float4* g4 = reinterpret_cast<float4*>(g);
+    float4* m4 = reinterpret_cast<float4*>(ms);
+    float4* o4 = reinterpret_cast<float4*>(mom);
+    for (long i = blockIdx.x * 256L + threadIdx.x; i < P4; i += (long)gridDim.x * 256L) {
+        float4 pp = p4[i], gg = g4[i], mm = m4[i], oo = o4[i];
+        rmsprop_elem(pp.x, gg.x, mm.x, oo.x, lr, omd, momentum, eps, total_weight, scale);
+        rmsprop_elem(pp.y, gg.y, mm.y, oo.y, lr, omd, momentum, eps, total_weight, scale);
+        rmsprop_elem(pp.z, gg.z, mm.z, oo.z, lr, omd, momentum, eps, total_weight, scale);
+        rmsprop_elem(pp.w, gg.w, mm.w, oo.w, lr, omd, momentum, eps, total_weight, scale);
+        g4[i] = gg; m4[i] = mm; o4[i] = oo; p4[i] = pp;
+    }
+    if (blockIdx.x == 0 && threadIdx.x < (int)(P & 3)) {          // tail
+        const long i = P4 * 4 + threadIdx.x;
+        float pp = p[i], gg = g[i], mm = ms[i], oo = mom[i];
+        rmsprop_elem(pp, gg, mm, oo, lr, omd, momentum, eps, total_weight, scale);
+        g[i] = gg; ms[i] = mm; mom[i] = oo; p[i] = pp;
+    }
+}
+
+namespace mrl {
+// as adam_clip_apply: `ready_part` / `ready_npart` are the gradient producer's sum-of-squares partials (nullptr: one extra pass)
+int rmsprop_clip_apply(float* params, float* grads, float* ms, float* mom, long P, float lr, const float* lr_dev, float decay,
+                       float momentum, float eps, float max_grad_norm, float total_weight, float* gnorm_out, void* scratch,
+                       const double* ready_part, int ready_npart, hipStream_t st) {
+    if (!params || !grads || !ms || !mom || P <= 0 || total_weight <= 0.f) return MRL_EINVAL;
+    if (!vec16(params) || !vec16(grads) || !vec16(ms) || !vec16(mom)) return MRL_EINVAL;
+    if (max_grad_norm >= 0.f && !ready_part && !scratch) return MRL_EINVAL;
+    const bool fused = ready_part != nullptr && max_grad_norm >= 0.f;
+    ProfScope ps("clip+rmsprop", 0.0, (max_grad_norm >= 0.f && !fused ? 32.0 : 28.0) * P, st);
+    const double* part = ready_part;
+    int npart = ready_npart;
+    if (max_grad_norm >= 0.f && !ready_part) {
+        npart = (int)min((P + 4095) / 4096, (long)ADAM_MAX_PART);
+        hipLaunchKernelGGL(sumsq_kernel, dim3(npart), dim3(256), 0, st, grads, P, total_weight, (double*)scratch);
+        MRL_LAUNCH_CHECK();
+        part = (const double*)scratch;
+    }
+    const int blocks = (int)min((P / 4 + 255) / 256 + 1, (long)2048);
+    hipLaunchKernelGGL(rmsprop_kernel, dim3(blocks), dim3(256), 0, st, params, grads, ms, mom, P, lr, decay, momentum, eps,
+                       max_grad_norm, total_weight, part, npart, gnorm_out, lr_dev);
+    MRL_LAUNCH_CHECK();
+    return 0;
+}
+}  // namespace mrl
+
+extern "C" int mrl_rmsprop_clip_step(float* params, float* grads, float* ms, float* mom, long P, float lr, float decay,
+                                     float momentum, float eps, float max_grad_norm, float total_weight, float* gnorm_out,
+                                     void* scratch, void* stream) {
+    return rmsprop_clip_apply(params, grads, ms, mom, P, lr, nullptr, decay, momentum, eps, max_grad_norm, total_weight,
+                              gnorm_out, scratch, nullptr, 0, (hipStream_t)stream);
+}
+
+extern "C" int mrl_rmsprop_clip_step_dev(float* params, float* grads, float* ms, float* mom, long P, const float* lr_dev,
+                                         float decay, float momentum, float eps, float max_grad_norm, float total_weight,
+                                         float* gnorm_out, void* scratch, void* stream) {
+    if (!lr_dev) return MRL_EINVAL;
+    return rmsprop_clip_apply(params, grads, ms, mom, P, 0.f, lr_dev, decay, momentum, eps, max_grad_norm, total_weight,
+                              gnorm_out, scratch, nullptr, 0, (hipStream_t)stream);
 }

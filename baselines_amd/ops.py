@@ -35,6 +35,42 @@ def gae(rewards, values, dones, last_values, last_dones, gamma, lam, want_advs=F
     return (ret, adv) if want_advs else ret
 
 
+def nstep_returns(rewards, dones, last_values, last_dones, gamma, out=None):
+    """a2c/runner.py:58-71 on device: n-step discounted returns bootstrapped from last_values (bit-exact).
+    rewards f32 [T,N], dones u8/bool [T,N] (entering each step), last_values f32 [N], last_dones u8/bool [N]."""
+    _lib.require_gpu()
+    rewards = _dev(rewards)
+    T, N = rewards.shape
+    dones = _dev(dones.view(torch.uint8) if dones.dtype == torch.bool else dones)
+    last_dones = _dev(last_dones.view(torch.uint8) if last_dones.dtype == torch.bool else last_dones)
+    last_values = _dev(last_values)
+    assert rewards.dtype == last_values.dtype == torch.float32 and last_values.shape == (N,)
+    assert dones.dtype == torch.uint8 and dones.shape == (T, N) and last_dones.shape == (N,)
+    if out is not None:
+        assert out.shape == rewards.shape and out.dtype == torch.float32 and out.is_contiguous() and out.device == rewards.device
+    ret = out if out is not None else torch.empty_like(rewards)
+    check(_lib.load().mrl_nstep_returns(ptr(rewards), ptr(dones), ptr(last_values), ptr(last_dones), float(gamma), ptr(ret),
+                                        T, N, stream_ptr()), 'mrl_nstep_returns')
+    return ret
+
+
+def rmsprop_clip_step(params, grads, ms, mom, lr, decay, momentum, eps, max_grad_norm, scratch, gnorm_out=None,
+                      total_weight=1.0, lr_dev=None):
+    """a2c.py:76-86: clip_by_global_norm -> TF-1 RMSProp, one kernel (+ one norm pass).  lr_dev: f32 [1] device step size."""
+    _lib.require_gpu()
+    P = params.numel()
+    mgn = -1.0 if max_grad_norm is None else float(max_grad_norm)
+    lib = _lib.load()
+    if lr_dev is not None:
+        check(lib.mrl_rmsprop_clip_step_dev(ptr(params), ptr(grads), ptr(ms), ptr(mom), P, ptr(lr_dev), float(decay),
+                                            float(momentum), float(eps), mgn, float(total_weight), ptr(gnorm_out),
+                                            ptr(scratch), stream_ptr()), 'mrl_rmsprop_clip_step_dev')
+    else:
+        check(lib.mrl_rmsprop_clip_step(ptr(params), ptr(grads), ptr(ms), ptr(mom), P, float(lr), float(decay),
+                                        float(momentum), float(eps), mgn, float(total_weight), ptr(gnorm_out),
+                                        ptr(scratch), stream_ptr()), 'mrl_rmsprop_clip_step')
+
+
 def gather_rows(src, idx, T, N):
     """`arr[mbinds]` of the reference (ppo2.py:162-164) on a time-major device field.
     src [T*N, ...] (time-major rows), idx int64 env-major flat indices [B] -> [B, ...]."""
@@ -246,3 +282,12 @@ class DeviceModel(object):
                                             float(cliprange), float(ent_coef), float(vf_coef), ptr(grads_out),
                                             ptr(stats_out), ptr(self.workspace), self.workspace.numel(), self.chunk,
                                             stream_ptr()), 'mrl_model_grad_micro')
+
+    def grad_a2c(self, params, obs, actions, returns, values, masks, states, nseq, idx, B, T, N, ent_coef, vf_coef,
+                 grads_out, stats_out):
+        """a2c.py:57-68 minus the optimizer: flat dloss/dparams + [pg_loss, vf_loss, entropy]."""
+        check(self.lib.mrl_model_grad_a2c(self.handle, ptr(params), ptr(obs), ptr(actions), ptr(returns), ptr(values),
+                                          ptr(masks), ptr(states), int(nseq), ptr(idx), int(B), int(T), int(N),
+                                          float(ent_coef), float(vf_coef), ptr(grads_out), ptr(stats_out),
+                                          ptr(self.workspace), self.workspace.numel(), self.chunk, stream_ptr()),
+              'mrl_model_grad_a2c')

@@ -181,7 +181,8 @@ class Runner(AbstractEnvRunner):
         process talk to the runtime while we would be capturing) keep the eager loop."""
         from .model import Model
         from ..common.vec_env.synthetic_vec_env import SyntheticVecEnv
-        return (type(self.model) is Model and not self.model.multi and not self.recurrent
+        stock = type(self.model) is Model or vars(type(self.model)).get('stock_act_side', False)   # (a2c.Model: same act side)
+        return (stock and not self.model.multi and not self.recurrent
                 and type(self.env) is SyntheticVecEnv and not _lib.prof_enabled()
                 and os.environ.get('MRL_ROLLOUT_GRAPH', '1') != '0' and self._graph is not False)
 

@@ -49,6 +49,14 @@ int mrl_gae(const float* rew, const float* val, const uint8_t* done, const float
             const uint8_t* last_done, double gamma, double lam, float* adv_out, float* ret_out,
             int T, int N, void* stream);
 
+/* ---- A2C n-step discounted returns --- a2c/runner.py:49-75, a2c/utils.py:147-153 (discount_with_dones) ------
+ * rew f32 [T][N]; done u8 [T][N] (flag ENTERING step t, as mrl_gae); last_val f32 [N]; last_done u8 [N].
+ * Per env, f64 carry in the reference's order: r = 0; if !last_done: r = last_val + (gamma*r)*1; then for t = T-1..0
+ * r = rew[t] + (gamma*r)*(1 - done_after_t) with done_after_t = done[t+1] (last_done for t = T-1); ret[t] = f32(r).
+ * gamma <= 0: ret = rew (runner.py:58).  Bit-exact vs the reference, sign of zero included. */
+int mrl_nstep_returns(const float* rew, const uint8_t* done, const float* last_val, const uint8_t* last_done,
+                      double gamma, float* ret_out, int T, int N, void* stream);
+
 /* ---- K4: standalone minibatch gather --- ppo2/ppo2.py:162-164 `arr[mbinds]` ---------------
  * src time-major rows [T*N][row_bytes]; idx env-major flat indices int64 [B]; dst [B][row_bytes]. */
 int mrl_gather_rows(const void* src, const int64_t* idx, void* dst, int B, int T, int N,
@@ -196,6 +204,43 @@ int mrl_model_train_step(const mrl_model* m, float* params, float* grads, float*
                          float beta2, float eps, float max_grad_norm, float total_weight, float* stats_out,
                          float* gnorm_out, void* workspace, size_t workspace_bytes, int chunk, void* stream);
 
+/* ---- A2C gradient on the whole rollout --- a2c/a2c.py:57-68,88-109 -----------------------------------------------
+ * Fields as mrl_model_grad (time-major, idx = env-major flat indices or NULL for rows 0..B-1).  adv = returns - values
+ * (not normalised); loss = mean(adv*neglogp) - ent_coef*mean(H) + vf_coef*mean((v - R)^2).  grads_out f32 [P] is
+ * dloss/dparams (not clipped); stats_out f32 [3] = [policy_loss, value_loss, policy_entropy] (a2c.py:103-106).
+ * Feedforward policies pass masks = states = NULL.  Recurrent policies: nseq whole trajectories as mrl_model_grad_rnn
+ * (states f32 [nseq][2*nlstm] before the first step, masks u8 = done flags entering each step).
+ * A communicator attached to the model (mrl_model_attach_comm): MRL_EUNSUP (the reference's A2C has no MPI path). */
+int mrl_model_grad_a2c(const mrl_model* m, const float* params, const void* obs, const void* actions,
+                       const float* returns, const float* values, const uint8_t* masks, const float* states,
+                       int nseq, const int64_t* idx, int B, int T, int N, float ent_coef, float vf_coef,
+                       float* grads_out, float* stats_out, void* workspace, size_t workspace_bytes, int chunk,
+                       void* stream);
+
+/* ---- clip_by_global_norm -> RMSProp --- a2c/a2c.py:76-86; TF 1.x ApplyRMSProp (momentum, not centered) ----------
+ * grads := grads / total_weight * scale, scale = c*min(1/gn, 1/c) (max_grad_norm < 0: none), then per element in f32:
+ *   ms  += (g*g - ms) * (1 - decay);   mom = mom*momentum + (lr*g) / sqrt(ms + eps);   p -= mom.
+ * The caller initialises ms to ONES and mom to zeros (TF's slot initialisers).  `grads` is left holding the clipped
+ * gradient.  scratch: >= mrl_adam_scratch_bytes(P).  gnorm_out f32 [1] may be NULL.  _dev: lr read from device memory
+ * (f32 [1]) when the kernel runs, so the launch can sit in a replayed hipGraph. */
+int mrl_rmsprop_clip_step(float* params, float* grads, float* ms, float* mom, long P, float lr, float decay,
+                          float momentum, float eps, float max_grad_norm, float total_weight, float* gnorm_out,
+                          void* scratch, void* stream);
+int mrl_rmsprop_clip_step_dev(float* params, float* grads, float* ms, float* mom, long P, const float* lr_dev,
+                              float decay, float momentum, float eps, float max_grad_norm, float total_weight,
+                              float* gnorm_out, void* scratch, void* stream);
+
+/* ---- A2C Model.train in one call --- a2c/a2c.py:88-109 ------------------------------------------------------------
+ * = mrl_model_grad_a2c followed by mrl_rmsprop_clip_step on the same stream; for feedforward policies the global-norm
+ * partials come from the reductions that write the gradient (as mrl_model_train_step).  lr_dev != NULL: step size
+ * read from device memory, else `lr` (host f32).  A communicator attached: MRL_EUNSUP. */
+int mrl_model_train_step_a2c(const mrl_model* m, float* params, float* grads, float* rms_ms, float* rms_mom,
+                             const void* obs, const void* actions, const float* returns, const float* values,
+                             const uint8_t* masks, const float* states, int nseq, const int64_t* idx, int B,
+                             int T, int N, float ent_coef, float vf_coef, float lr, const float* lr_dev,
+                             float decay, float momentum, float eps, float max_grad_norm, float* stats_out,
+                             float* gnorm_out, void* workspace, size_t workspace_bytes, int chunk, void* stream);
+
 /* ---- minibatch advantage statistics ahead of time --- ppo2/model.py:136-139 for every minibatch of an epoch at once
  * (ppo2.py:157-166: the epoch's permutation is known before its first step).  idx int64 [nmb][B] env-major indices;
  * out f32 [nmb][2] = (mean, std) of returns - values over each minibatch, formed exactly like the fused MLP step kernel
@@ -227,7 +272,7 @@ int mrl_allreduce_grads(mrl_comm* c, float* grads, long P, void* stream);
 /* in-place broadcast of nbytes from `root` (parameters, Adam slots; mpi_util.py:15-26), asynchronous on `stream` */
 int mrl_broadcast_state(mrl_comm* c, void* buf, size_t nbytes, int root, void* stream);
 /* Attach (comm != NULL) / detach (NULL) a communicator: afterwards mrl_model_grad, mrl_model_grad_micro and
- * mrl_model_train_step return the rank-weighted SUM over ranks of the gradient.  The all-reduce is issued from
+ * mrl_model_train_step return the rank-weighted SUM over ranks of the gradient (the A2C entries refuse it: MRL_EUNSUP).  The all-reduce is issued from
  * inside the backward pass on the communicator's own stream -- the tail of the flat gradient (fc1 + heads, 95 % of
  * NatureCNN's parameters) as soon as fc1's weight gradient is complete, the rest at the end -- and the compute
  * stream is made to wait for it before the call returns (stream order; no host synchronisation).  The division by
