@@ -33,6 +33,19 @@ class QNetDesc(ctypes.Structure):
                 ('convs', (c_int * 3) * 4), ('nhidden', c_int), ('hiddens', c_int * 4), ('dueling', c_int), ('nact', c_int),
                 ('layer_norm', c_int), ('body_layer_norm', c_int)]
 
+class DDPGDesc(ctypes.Structure):
+    """mirror of mrl_ddpg_desc (include/mrl.h)"""
+    _fields_ = [('ob_dim', c_int), ('nact', c_int), ('num_layers', c_int), ('num_hidden', c_int), ('activation', c_int),
+                ('layer_norm', c_int), ('normalize_observations', c_int), ('normalize_returns', c_int), ('popart', c_int)]
+
+
+class DDPGState(ctypes.Structure):
+    """mirror of mrl_ddpg_state (include/mrl.h): device pointers"""
+    _fields_ = [(n, c_void_p) for n in ('actor', 'critic', 'target_actor', 'target_critic', 'actor_m', 'actor_v', 'critic_m',
+                                        'critic_v', 'obs_rms', 'ret_rms', 'obs0', 'actions', 'rewards', 'obs1', 'terminals1',
+                                        'ring_pos')] + [('limit', c_long)]
+
+
 PD_CATEGORICAL, PD_DIAG_GAUSSIAN, PD_MULTICATEGORICAL, PD_BERNOULLI = 0, 1, 2, 3
 OB_F32, OB_U8 = 0, 1
 ACT_NONE, ACT_RELU, ACT_TANH = 0, 1, 2
@@ -133,6 +146,18 @@ SIGNATURES = {
     'mrl_allreduce_grads': (c_int, [c_void_p, c_void_p, c_long, c_void_p]),
     'mrl_broadcast_state': (c_int, [c_void_p, c_void_p, c_size_t, c_int, c_void_p]),
     'mrl_model_attach_comm': (c_int, [c_void_p, c_void_p, c_float]),
+    'mrl_ddpg_num_params': (c_long, [ctypes.POINTER(DDPGDesc), c_int]),
+    'mrl_ddpg_workspace_bytes': (c_size_t, [ctypes.POINTER(DDPGDesc), c_int]),
+    'mrl_ddpg_train_step': (c_int, [ctypes.POINTER(DDPGDesc), ctypes.POINTER(DDPGState), c_void_p, c_int, c_void_p, c_float,
+                                    c_double, c_float, c_float, c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    'mrl_ddpg_soft_update': (c_int, [ctypes.POINTER(DDPGDesc), ctypes.POINTER(DDPGState), c_double, c_void_p]),
+    'mrl_ddpg_act': (c_int, [ctypes.POINTER(DDPGDesc), ctypes.POINTER(DDPGState)] + [c_void_p] * 4 + [c_int] +
+                     [c_void_p] * 3 + [c_size_t, c_void_p]),
+    'mrl_ddpg_store': (c_int, [ctypes.POINTER(DDPGDesc), ctypes.POINTER(DDPGState)] + [c_void_p] * 5 + [c_int, c_float,
+                                                                                                        c_void_p]),
+    'mrl_ddpg_perturb': (c_int, [ctypes.POINTER(DDPGDesc), c_void_p, c_void_p, c_void_p, c_float, c_void_p]),
+    'mrl_ddpg_policy_distance': (c_int, [ctypes.POINTER(DDPGDesc), ctypes.POINTER(DDPGState), c_void_p, c_void_p, c_int,
+                                         c_void_p, c_void_p, c_size_t, c_void_p]),
     'mrl_prof_enable': (c_int, [c_int]),
     'mrl_prof_num_labels': (c_int, []),
     'mrl_prof_get': (c_int, [c_int, c_char_p, c_int, ctypes.POINTER(c_long), ctypes.POINTER(c_double),

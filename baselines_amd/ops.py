@@ -291,3 +291,79 @@ class DeviceModel(object):
                                           float(ent_coef), float(vf_coef), ptr(grads_out), ptr(stats_out),
                                           ptr(self.workspace), self.workspace.numel(), self.chunk, stream_ptr()),
               'mrl_model_grad_a2c')
+
+
+class DDPGKernels(object):
+    """The DDPG entry points of include/mrl.h (mrl_ddpg_*) for one network configuration, with their workspace."""
+
+    def __init__(self, *, ob_dim, nact, num_layers=2, num_hidden=64, activation='tanh', layer_norm=False,
+                 normalize_observations=True, normalize_returns=False, popart=False, max_batch=1024, device=None):
+        _lib.require_gpu()
+        self.lib = _lib.load()
+        d = _lib.DDPGDesc()
+        d.ob_dim, d.nact, d.num_layers, d.num_hidden = int(ob_dim), int(nact), int(num_layers), int(num_hidden)
+        d.activation = {'tanh': _lib.ACT_TANH, 'relu': _lib.ACT_RELU}[activation]
+        d.layer_norm, d.normalize_observations = int(bool(layer_norm)), int(bool(normalize_observations))
+        d.normalize_returns, d.popart = int(bool(normalize_returns)), int(bool(popart))
+        self.desc = d
+        self.Pa = int(self.lib.mrl_ddpg_num_params(ctypes.byref(d), 0))
+        self.Pc = int(self.lib.mrl_ddpg_num_params(ctypes.byref(d), 1))
+        if self.Pa < 0:
+            raise _lib.MrlError('DDPG configuration outside the supported hot path (include/mrl.h, mrl_ddpg_desc): %s' %
+                                dict((f, getattr(d, f)) for f, _ in d._fields_))
+        self.device = torch.device(device or 'cuda')
+        self.max_batch = 0
+        self.workspace = None
+        self.frozen = False         # set by whoever captures a launch graph over this workspace
+        self.reserve(max_batch)
+
+    def reserve(self, rows):
+        """grow the workspace to serve train steps / act calls of up to `rows` rows (act calls of more rows are served in
+        chunks); a no-op once `frozen`"""
+        rows = int(rows)
+        if rows <= self.max_batch or self.frozen:
+            return                  # once a graph has captured the workspace's address it is never reallocated
+        nbytes = int(self.lib.mrl_ddpg_workspace_bytes(ctypes.byref(self.desc), rows))
+        if nbytes == 0:
+            raise _lib.MrlError('mrl_ddpg_workspace_bytes: unsupported batch of %d rows' % rows)
+        self.workspace = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        self.max_batch = rows
+
+    def train_step(self, state, idx, neg_alpha, gamma, tau, critic_l2_reg, clip_norm, soft_update, losses_out,
+                   grads_out=None):
+        B = idx.numel()
+        check(self.lib.mrl_ddpg_train_step(ctypes.byref(self.desc), ctypes.byref(state), ptr(idx), B, ptr(neg_alpha),
+                                           float(gamma), float(tau), float(critic_l2_reg),
+                                           -1.0 if clip_norm is None else float(clip_norm), int(bool(soft_update)),
+                                           ptr(grads_out), ptr(losses_out), ptr(self.workspace), self.workspace.numel(),
+                                           stream_ptr()), 'mrl_ddpg_train_step')
+
+    def soft_update(self, state, tau):
+        check(self.lib.mrl_ddpg_soft_update(ctypes.byref(self.desc), ctypes.byref(state), float(tau), stream_ptr()),
+              'mrl_ddpg_soft_update')
+
+    def act(self, state, obs, perturbed=None, actions_in=None, noise=None, actions_out=None, q_out=None):
+        n = obs.shape[0]
+        self.reserve(min(n, 1024))
+        step = self.max_batch
+        for r0 in range(0, n, step):
+            r1 = min(n, r0 + step)
+            check(self.lib.mrl_ddpg_act(ctypes.byref(self.desc), ctypes.byref(state), ptr(perturbed), ptr(obs[r0:r1]),
+                                        ptr(None if actions_in is None else actions_in[r0:r1]), ptr(noise), r1 - r0,
+                                        ptr(None if actions_out is None else actions_out[r0:r1]),
+                                        ptr(None if q_out is None else q_out[r0:r1]), ptr(self.workspace),
+                                        self.workspace.numel(), stream_ptr()), 'mrl_ddpg_act')
+
+    def store(self, state, obs0, action, reward, obs1, terminal1, reward_scale):
+        check(self.lib.mrl_ddpg_store(ctypes.byref(self.desc), ctypes.byref(state), ptr(obs0), ptr(action), ptr(reward),
+                                      ptr(obs1), ptr(terminal1), int(obs0.shape[0]), float(reward_scale), stream_ptr()),
+              'mrl_ddpg_store')
+
+    def perturb(self, actor, perturbed, noise, stddev):
+        check(self.lib.mrl_ddpg_perturb(ctypes.byref(self.desc), ptr(actor), ptr(perturbed), ptr(noise), float(stddev),
+                                        stream_ptr()), 'mrl_ddpg_perturb')
+
+    def policy_distance(self, state, perturbed, idx, out):
+        check(self.lib.mrl_ddpg_policy_distance(ctypes.byref(self.desc), ctypes.byref(state), ptr(perturbed), ptr(idx),
+                                                idx.numel(), ptr(out), ptr(self.workspace), self.workspace.numel(),
+                                                stream_ptr()), 'mrl_ddpg_policy_distance')

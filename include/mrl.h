@@ -385,6 +385,72 @@ int mrl_qnet_adam_step(const mrl_qnet* q, float* params, float* grads, float* ad
                        const float* alpha_dev, float beta1, float beta2, float eps, float grad_norm_clipping,
                        void* workspace, size_t workspace_bytes, int batch, void* stream);
 
+/* ---- DDPG --- ddpg/ddpg_learner.py, ddpg/memory.py, ddpg/models.py, common/mpi_running_mean_std.py ---------------------
+ * Networks: actor mlp(obs) -> dense(nact) -> tanh, critic mlp(concat(normalized obs, action)) -> output(1)
+ * (ddpg/models.py:27-51).  Flat f32 parameters per network in TF creation order: mlp_fc<i>/w [nin][nh], mlp_fc<i>/b [nh],
+ * (LayerNorm[_i]/beta, LayerNorm[_i]/gamma [nh] when layer_norm) for each layer, then the final kernel [nh][nout] and bias
+ * [nout].  mrl_ddpg_num_params(d, 0 = actor | 1 = critic).
+ * Supported (else MRL_EUNSUP): num_layers 1..4, num_hidden a multiple of 32 in 32..256, tanh | relu, ob_dim 1..4096,
+ * nact 1..32, batch 1..1024.  The reference's observation_range (-5, 5), action_range (-1, 1) and return_range (-inf, inf)
+ * are built in.
+ * State: obs_rms f64 [2*ob_dim + 1] = runningsum | runningsumsq | count; ret_rms f64 [3] (sum, sumsq, count; only with
+ * normalize_returns); replay ring f32 [limit][...] per field with ring_pos int64 [2] = (start, length) on the device
+ * (memory.py:4-35: append at (start + length - 1) % limit, batch rows at (start + idx) % limit). */
+typedef struct mrl_ddpg_desc {
+    int ob_dim, nact, num_layers, num_hidden;
+    int activation;                 /* MRL_ACT_TANH | MRL_ACT_RELU */
+    int layer_norm;
+    int normalize_observations;     /* 0: obs only clipped to [-5, 5] */
+    int normalize_returns, popart;
+} mrl_ddpg_desc;
+typedef struct mrl_ddpg_state {
+    float *actor, *critic, *target_actor, *target_critic;
+    float *actor_m, *actor_v, *critic_m, *critic_v;           /* MpiAdam slots, f32 */
+    double *obs_rms, *ret_rms;
+    float *obs0, *actions, *rewards, *obs1, *terminals1;      /* ring fields [limit][ob_dim | nact | 1] */
+    int64_t* ring_pos;
+    long limit;
+} mrl_ddpg_state;
+long   mrl_ddpg_num_params(const mrl_ddpg_desc* d, int net);
+/* workspace of a train step / act call / policy distance of up to B rows (one buffer serves all three) */
+size_t mrl_ddpg_workspace_bytes(const mrl_ddpg_desc* d, int B);
+/* One DDPG.train() (ddpg_learner.py:268-309 with setup_actor_optimizer, setup_critic_optimizer, setup_popart) in ONE launch:
+ * gather the batch at host-drawn idx int64 [B] (indices into [0, nb_entries)), normalise + clip obs0 / obs1 with obs_rms,
+ * target_Q = r + (1 - d) * gamma * denorm(Q'(obs1, mu'(obs1))), [pop-art: ret_rms.update(target_Q) in f64, renormalise the
+ * output layer of critic and target critic], critic loss mse(Q, normalize(target_Q)) + critic_l2_reg * sum 0.5 |w|^2 over
+ * the critic mlp_fc<i>/w, actor loss -mean(denorm(Q(obs0, mu(obs0)))) through the critic of before the step, per-variable
+ * clip_by_norm(clip_norm) when clip_norm > 0, then MpiAdam (common/mpi_adam.py:38-41; beta1 0.9, beta2 0.999, eps 1e-8) for
+ * each network.  neg_alpha: device f32 [2] = -a for the actor and the critic, a = lr*sqrt(1-beta2^t)/(1-beta1^t) (read when
+ * the kernel runs, so captured steps replay with new values).  soft_update != 0: also update_target_net()
+ * (ddpg_learner.py:36-47) with f32(tau) and f32(1 - tau).  grads_out f32 [Pa + Pc] (may be NULL): the clipped gradients
+ * Adam consumed.  losses_out f32 [2] = critic_loss, actor_loss. */
+int mrl_ddpg_train_step(const mrl_ddpg_desc* d, const mrl_ddpg_state* s, const int64_t* idx, int B, const float* neg_alpha,
+                        float gamma, double tau, float critic_l2_reg, float clip_norm, int soft_update, float* grads_out,
+                        float* losses_out, void* workspace, size_t workspace_bytes, void* stream);
+/* update_target_net() alone: target <- (1 - tau) * target + tau * var for actor and critic */
+int mrl_ddpg_soft_update(const mrl_ddpg_desc* d, const mrl_ddpg_state* s, double tau, void* stream);
+/* DDPG.step (ddpg_learner.py:239-257) for n rows of raw obs f32 [n][ob_dim]: actions_out f32 [n][nact] from the actor, or
+ * from perturbed_actor when it is not NULL; q_out f32 [n] = denorm(critic(obs, actor(obs))) from the UNPERTURBED actor
+ * (critic_with_actor_tf), or denorm(critic(obs, actions_in)) when actions_in f32 [n][nact] is given (critic_tf,
+ * get_stats).  noise: f64 [nact] added to every row as `action += noise` does (NULL: none); then clip to [-1, 1].
+ * Either output may be NULL. */
+int mrl_ddpg_act(const mrl_ddpg_desc* d, const mrl_ddpg_state* s, const float* perturbed_actor, const float* obs,
+                 const float* actions_in, const double* noise, int n, float* actions_out, float* q_out, void* workspace,
+                 size_t workspace_bytes, void* stream);
+/* store_transition (ddpg_learner.py:259-266) for n rows in order: ring append of (obs0, action, reward * reward_scale, obs1,
+ * terminal1 u8 -> 1.f / 0.f), and, with normalize_observations, obs_rms.update(obs0[b]) one row at a time (f64 sums in row
+ * order, count += 1 per row): bit-identical to the sequential update. */
+int mrl_ddpg_store(const mrl_ddpg_desc* d, const mrl_ddpg_state* s, const float* obs0, const float* action, const float* reward,
+                   const float* obs1, const uint8_t* terminal1, int n, float reward_scale, void* stream);
+/* get_perturbed_actor_updates (ddpg_learner.py:50-62): perturbed = actor + stddev * noise on every tensor except the
+ * LayerNorm ones, which are copied.  noise f32 [Pa] ~ N(0, 1) from the caller (stands in for tf.random_normal). */
+int mrl_ddpg_perturb(const mrl_ddpg_desc* d, const float* actor, float* perturbed, const float* noise, float stddev,
+                     void* stream);
+/* adaptive_policy_distance (ddpg_learner.py:168-173): distance_out f32 [1] = sqrt(mean((actor(o) - perturbed(o))^2)) over
+ * the ring rows at idx int64 [B] (normalised, clipped obs0). */
+int mrl_ddpg_policy_distance(const mrl_ddpg_desc* d, const mrl_ddpg_state* s, const float* perturbed_actor, const int64_t* idx,
+                             int B, float* distance_out, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- synthetic device-resident VecEnv (bench/test data source) ----------------------------
  * Stands where gym environments stand in the reference (common/vec_env/): lock-step stepping with
  * AUTO-RESET on done (subproc_vec_env.py:8-12) and Monitor-style episode bookkeeping
